@@ -9,8 +9,14 @@ One STEP = the DINO fwd+loss of `--clips` multi-crop video clips per GPU (config
   column sum is all-reduced over RCCL when N > 1.
 value = clips/s over ALL ranks (weak scaling: `--clips` per GPU), inputs resident in HBM.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W]
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
         (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step,
+step_roofline).  --dump-outputs DIR also writes what the last timed step computed as DIR/*.npy.
+--full adds every other measurement to the same line: the config-3 SSL training step, the
+per-kernel roofline probe, the other configurations (backbone alone, fp32 parity mode, configs 4 /
+5, Swin-T training, frame scoring) and the CPU baseline; the --no-* options drop single legs of it.
 """
 import argparse
 import json
@@ -537,6 +543,28 @@ def other_configs(args, device):
     return res
 
 
+# ----------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET_BYTES = 60 << 20       # array bytes of one dump: under 64 MB (10^6) with the .npy headers
+
+
+def dump_outputs(path, tensors):
+    """Write every tensor of `tensors` (name -> device tensor) as path/<name>.npy in float32.  The
+    arrays share DUMP_BUDGET_BYTES equally: one whose float32 form is larger than its share is cut
+    to a fixed, seeded sample of its rows (ascending row order), the same rows in every run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(tensors), 1)
+    for name, t in tensors.items():
+        a = t.detach().float().cpu().numpy()
+        a = a.reshape(1) if a.ndim == 0 else a
+        if a.nbytes > share:
+            a = a.reshape(a.shape[0], -1)
+            keep = max(1, share // max(a[0].nbytes, 1))
+            if keep < a.shape[0]:
+                a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+            a = a[:, :share // 4]              # a single row above the share: its leading part
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # ----------------------------------------------------------------- main
 def launch_ranks(args):
     """`bench.py --gpus N` (N > 1) outside torch.distributed.run: start N ranks of this script
@@ -564,6 +592,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--clips", type=int, default=8, help="multi-crop clips per GPU per step (config 2: 8)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the config-3 training step, the per-kernel roofline probe, the other "
+                         "configurations and the CPU baseline (a plain run times the fwd+loss steps only); "
+                         "the --no-* options below drop single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, student / teacher "
+                         "logits, updated center) as DIR/<name>.npy in float32 (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel HIP-event probe")
     ap.add_argument("--serial", action="store_true",
@@ -607,7 +642,7 @@ def main():
     # config 3 first: measured after the forward's HIP-graph capture and replays, the same training
     # step ran 86 instead of 99 clips/s (tools/train_step.py alone: 99-100)
     train_res = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         train_res = train_bench(args, device, rank, world, args.train_steps, 2)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -623,6 +658,7 @@ def main():
     student.concurrent_groups = teacher.concurrent_groups = not args.serial
 
     dino_loss.defer_center_update = True   # center all-reduce + EMA outside the graph
+    last_logits = {}                       # the step's student / teacher logits, for --dump-outputs
 
     def forward_loss(concurrent=not args.serial):
         student.concurrent_groups = teacher.concurrent_groups = concurrent
@@ -632,6 +668,7 @@ def main():
             # student: 2 backbone calls (224 / 96 groups) + head on (2+6)*clips rows; teacher:
             # 1 backbone call + head on 2*clips rows -- three independent calls, overlapped
             s_out, t_out = dino_forward(student, teacher, crops, concurrent=concurrent)
+            last_logits["student_logits"], last_logits["teacher_logits"] = s_out, t_out
             return dino_loss(s_out, t_out, 0)
 
     def center_update():
@@ -651,7 +688,7 @@ def main():
     # with HIP events on its stream; kernels sharing the chip with another stream would read
     # long), so the roofline is each kernel's own time -- same command as the rocprof summary
     probe = None
-    if not args.no_probe:
+    if args.full and not args.no_probe:
         ops.probe_enable(PROBE_GEMM, 1 << 16)
         for _ in range(min(args.steps, 5)):
             step(concurrent=False)
@@ -695,6 +732,9 @@ def main():
     loss_val = float(loss.item())
     if not np.isfinite(loss_val):
         raise SystemExit("bench: non-finite DINO loss %r -- the measured step is not valid" % loss_val)
+    if args.dump_outputs and rank == 0:
+        # with the captured graph these are its static output buffers: the last replay's values
+        dump_outputs(args.dump_outputs, dict(last_logits, loss=loss, center=dino_loss.center))
 
     roofline = None
     if probe is not None:
@@ -786,9 +826,9 @@ def main():
            "rccl_ranks": world if ddist.backend() == "nccl" else 0}
     if train_res is not None:
         out["train_step"] = train_res
-    if rank == 0 and world == 1 and not args.no_other:
+    if args.full and rank == 0 and world == 1 and not args.no_other:
         out["other_configs"] = other_configs(args, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -82,7 +82,7 @@ def test_bench_multi_gpu_path_rehearsal(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     log = os.path.join(LOGDIR if os.path.isdir(LOGDIR) else str(tmp_path), "bench_dp2_rehearsal.log")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--shared-gpu",
-           "--steps", "2", "--warmup", "1", "--train-steps", "1", "--no-other", "--no-cpu-baseline"]
+           "--full", "--steps", "2", "--warmup", "1", "--train-steps", "1", "--no-other", "--no-cpu-baseline"]
     with open(log, "w") as f:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=f, text=True, timeout=420)
     assert r.returncode == 0, "bench --gpus 2 exited %d; stderr in %s:\n%s" % (

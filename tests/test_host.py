@@ -181,3 +181,25 @@ def test_teacher_step_settings_are_scoped():
     except RuntimeError:
         pass
     assert t.backbone.dsvt_streams == "auto" and t.backbone.fold_temporal_fc is True
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per tensor (0-d as shape (1,)), identical from call
+    to call, and an array above its share of the byte budget cut to the same seeded rows."""
+    import bench
+    x = torch.arange(64 * 512, dtype=torch.float32).reshape(64, 512).bfloat16()
+    outs = {"logits": x, "loss": torch.tensor(3.5), "center": torch.ones(1, 512)}
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(str(tmp_path / "a")))}
+    assert sorted(got) == ["center", "logits", "loss"] and all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["logits"], x.float().numpy())
+    assert got["loss"].shape == (1,) and got["loss"][0] == 3.5 and got["center"].shape == (1, 512)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * 16 * 512 * 4)       # 16 of the 64 rows fit
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    b, c = np.load(str(tmp_path / "b" / "logits.npy")), np.load(str(tmp_path / "c" / "logits.npy"))
+    np.testing.assert_array_equal(b, c)
+    rows = (b[:, 0] / 512).astype(int)
+    assert b.shape == (16, 512) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(b, x.float().numpy()[rows])
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))) <= 3 * 16 * 512 * 4 + 3 * 128

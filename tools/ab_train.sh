@@ -3,11 +3,11 @@
 # (diagnostic):  tools/ab_train.sh VAR "valA valB" [rounds]
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out; export TMPDIR=/tmp
+OUT=${OUT:-ab_out}; mkdir -p "$OUT"; export TMPDIR=/tmp
 var=$1; vals=$2; rounds=${3:-2}
 for r in $(seq 1 "$rounds"); do
   for v in $vals; do
-    env "$var=$v" timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-other --no-probe --steps 20 > gpurun_out/abt_${var}_${v}_$r.log 2>&1 || exit 1
-    echo "$var=$v round $r: $(tail -1 gpurun_out/abt_${var}_${v}_$r.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("fwd", d["value"], "train", d["train_step"]["value"])')"
+    env "$var=$v" timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --no-other --no-probe --steps 20 > $OUT/abt_${var}_${v}_$r.log 2>&1 || exit 1
+    echo "$var=$v round $r: $(tail -1 $OUT/abt_${var}_${v}_$r.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("fwd", d["value"], "train", d["train_step"]["value"])')"
   done
 done

@@ -23,8 +23,8 @@ for stage in "$@"; do
     model)   run model 1200 python -m pytest tests/test_gpu_model.py -q -rf -s ;;
     gputests) run gputests 1500 python -m pytest tests -m gpu -q -rf ;;
     smoke)   run smoke 600 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)   run bench 900 python bench.py && tail -n 1 "$OUT/bench.log" > "$OUT/bench.json" ;;
-    prof)    run prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --serial --no-graph --no-train --no-other &&
+    bench)   run bench 900 python bench.py --full && tail -n 1 "$OUT/bench.log" > "$OUT/bench.json" ;;
+    prof)    run prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --serial --no-graph --no-train --no-other &&
              python tools/prof_summary.py "$OUT/prof" --step-kernel loss_reduce > "$OUT/prof_summary.txt" ;;
     graphprof) run graphprof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/gprof" -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-probe --no-train --no-other &&
              python tools/prof_summary.py "$OUT/gprof" --step-kernel center_ema --last 15 > "$OUT/gprof_summary.txt" ;;
